@@ -14,11 +14,25 @@ The timed region holds K steps, the conversion of every game that ended in it an
 (utils.save_train_data's datasets, chunked: selfplay.TrainDataSink(path)).  `value` = whole-job node-expansions/s (one expansion = one evaluator call, MCTS.py:93); games/s,
 won games/s and sample rows/s sit beside it.  `roofline` = the dominant kernel, net_forward_kernel, against the fp32 MFMA peak.
 
-`variants` (one GPU; 2a on every rank): config 2a (table evaluator, fused kernel -- the parity-pinned no-net configuration)
-with its real bound, config 2b, the kernel micro-benchmarks.  `config5`: BASELINE configs[4] in miniature through
-train.evolve -- self-play at 800 simulations, one fit, the 24-game arena -- with wall seconds per phase (every rank takes
-part when N > 1).  Rank 0 finally times the CPU baselines on the host cores actually available to the process: the C oracle
-with the net as evaluator (`cpu_baseline`), with the table evaluator, and the reference-shaped pure-Python mirror with both.
+A plain run does only that: set-up, the untimed steps, the K timed steps, the line.  `--steps K` is the number of timed steps
+and `ms_per_step` the wall time of one of them (the timed region -- steps, final conversion, file -- over K).
+
+`--full` adds what the headline does not need, as runs of their own after it: the evaluator kernel alone (`roofline`'s
+isolated figures), `variants` (one GPU; 2a on every rank): config 2a (table evaluator, fused kernel -- the parity-pinned no-net
+configuration) with its real bound, config 2b, the kernel micro-benchmarks, config 1.  `config5`: BASELINE configs[4] in
+miniature through train.evolve -- self-play at 800 simulations, one fit, the 24-game arena -- with wall seconds per phase (every
+rank takes part when N > 1).  Rank 0 finally times the CPU baselines on the host cores actually available to the process: the
+C oracle with the net as evaluator (`cpu_baseline`), with the table evaluator, and the reference-shaped pure-Python mirror with
+both.
+
+`--dump-outputs DIR` writes, after the timed steps, the training rows the last harvest of the timed region handed to the
+sink (the games that ended in the last `--harvest-every` steps; if that harvest finished no won game, the last one before it
+that did -- `dump.harvest` in the line says which), in game-id order: DIR/board_x.npy (float32, [n, 7, 7, 7]),
+pi_y.npy, v_y.npy and game.npy (float64; the game id of every row); rank r > 0 writes DIR/rank<r>_<name>.npy.  A fixed,
+seeded sample of the rows is kept if they exceed 64 MB.  Such a run switches the advance kernel's TIME limits off for the
+whole run, timed steps included (its simulation budget stays; `config.advance_time_limits` is false and the steps are slower):
+a game's rows never depend on the limits, but with them which games end inside the timed steps depends on the clock --
+without them it depends on the arguments alone, so two builds can be compared array for array.
 
 Games shard over ranks by game id (rank r plays ids r, r+N, ...); the only collective of the path is the summary all-reduce
 after each timed region (RCCL; gloo when CCSP_BENCH_ONE_DEVICE=1 puts all ranks on one device for functional tests).
@@ -80,10 +94,10 @@ def net_roofline(n_pos, launch_ms, isolated_ms, wall_ms_per_launch, step_ms_per_
     own = launch_ms if launch_ms else wall_ms_per_launch
 
     def tflops(ms):
-        return flop / (ms * 1e-3) / 1e12
+        return flop / (ms * 1e-3) / 1e12 if ms else None        # (isolated_ms None: the burst was not run -- bench.py without --full)
 
     def frac(ms):
-        return tflops(ms) / MFMA_F32_PEAK_TFLOPS
+        return tflops(ms) / MFMA_F32_PEAK_TFLOPS if ms else None
     return {
         'bound': 'mfma', 'achieved': tflops(own), 'peak': MFMA_F32_PEAK_TFLOPS, 'unit': 'TFLOP/s', 'frac': frac(own), 'traffic': None,
         'useful_frac_by_step': asked_rows_per_s_per_gpu * NET_FLOP_PER_EVAL / 1e12 / MFMA_F32_PEAK_TFLOPS,
@@ -307,7 +321,19 @@ def config3(args, torch, rank, world, local, barrier):
     if w:
         model.load_weights(w)
     assert model.backend == 'hip', 'the evaluator must be the fused HIP kernel'
-    sink = sp.TrainDataSink()
+
+    class LastRowsSink(sp.TrainDataSink):
+        """--dump-outputs: the sink keeps a reference to the last chunk of rows it was handed in the timed region (no copy) and the
+        number of the harvest it came from (harvests counted from the first one of the timed region)"""
+        last = None
+        last_harvest = None
+        harvests = 0
+
+        def __call__(self, board_x, pi_y, v_y, games):
+            if not self.discard:
+                self.last, self.last_harvest = (board_x, pi_y, v_y, games), self.harvests
+            super().__call__(board_x, pi_y, v_y, games)
+    sink = LastRowsSink() if args.dump_outputs else sp.TrainDataSink()
     sink.discard = True
     # the id budget is never the limit: every slot can restart 64 times
     # the slots' first games begin spread over the untimed plies (all but the last twelve of them: every slot is playing well before the
@@ -316,12 +342,23 @@ def config3(args, torch, rank, world, local, barrier):
     span = max(0, args.spread_plies - 12) * (S + 1)
     run = sp.SelfPlayRun(model, n_games=G * 64, sims=S, seed=SEED, first_game=rank, game_stride=world, device=local, max_slots=G,
                          harvest_every=args.harvest_every, keep_records=False, sink=sink, stagger_span=span or None)
+    if args.dump_outputs:                               # (before the first step: a captured graph keeps the limits it was captured with)
+        for b_ in (run.b.parts if hasattr(run.b, 'parts') else [run.b]):
+            if getattr(b_, 'free_running', False):
+                b_.set_advance_limits(-1, 0, 0)         # simulation budget unchanged; no time cap, no deadline
+        absorb = run._absorb
+
+        def counted(parts):                             # (the run's worker thread: one call per harvest, in harvest order)
+            sink.harvests += 1
+            absorb(parts)
+        run._absorb = counted
     out_dir = tempfile.mkdtemp(prefix='ccsp-bench-')
     try:
         for _ in range(args.spread_plies + W):          # untimed: the first cohort of games spreads out, then the W warm-up steps
             run.play_ply()
         run.drain()
         sink.discard = False                            # rows of games that ended before the timed region are not its output
+        sink.harvests = 0
         sink.open(os.path.join(out_dir, 'data-for-iter-%d.h5' % rank))
         barrier()
         parts_ = run.b.parts if hasattr(run.b, 'parts') else [run.b]
@@ -331,14 +368,10 @@ def config3(args, torch, rank, world, local, barrier):
         c0 = run.counters()
         ru0 = resource.getrusage(resource.RUSAGE_SELF)   # this rank's host side (main thread + converter thread) over the timed region
         t0 = time.time()
-        steps = 0
-        while True:
-            for _ in range(K):
-                run.play_ply()
-            steps += K
-            torch.cuda.synchronize()
-            if time.time() - t0 >= args.min_seconds or K == 0:    # a timed region is never shorter than --min-seconds
-                break
+        steps = K
+        for _ in range(K):
+            run.play_ply()
+        torch.cuda.synchronize()
         t_play = time.time() - t0
         run.drain()                                     # the last harvest + the conversion of every game that ended
         t_drain = time.time() - t0 - t_play
@@ -360,7 +393,7 @@ def config3(args, torch, rank, world, local, barrier):
             raise RuntimeError('config 3 did not run on the free-running path')
         torch.cuda.synchronize()
         p0 = parts_[0]
-        if getattr(p0, 'free_running', False):          # one half-batch's requests as they stand: the isolated burst below evaluates these
+        if args.full and getattr(p0, 'free_running', False):      # one half-batch's requests as they stand: the isolated burst below evaluates these
             req_alone, moves_alone = p0._req.clone(), p0._moves.clone()
             asked_now = int((req_alone.view(torch.int32)[:, 8] != 0).sum())
         else:
@@ -369,8 +402,19 @@ def config3(args, torch, rank, world, local, barrier):
     finally:
         run.close()
         shutil.rmtree(out_dir, ignore_errors=True)
+    dumped = dump_rows(args.dump_outputs, sink, rank, world) if args.dump_outputs else None
     d = {k: c1[k] - c0[k] for k in c1}
     n_pos = run.n_slots // parts
+    info = dict(n_pos=n_pos, k_ms=None, ev_over_ms=None, parts=parts, weights=os.path.basename(w) if w else 'random-init', backend=model.backend,
+                steps=steps, rows_written=int(rows), file_bytes=size, t_play=t_play, t_drain=t_drain, t_write=t_write,
+                n_slots=run.n_slots, free_running=bool(getattr(run, 'free_running', False)), asked_in_isolated_batch=None,
+                net_in_pipeline_ms=(sorted(net_in_pipeline_ms)[len(net_in_pipeline_ms) // 2] if net_in_pipeline_ms else None),
+                net_in_pipeline_samples=len(net_in_pipeline_ms),
+                tree_in_pipeline_ms=(sorted(tree_in_pipeline_ms)[len(tree_in_pipeline_ms) // 2] if tree_in_pipeline_ms else None),
+                host_cpu_s=(ru1.ru_utime + ru1.ru_stime) - (ru0.ru_utime + ru0.ru_stime), peak_rss_mb=ru1.ru_maxrss / 1024.0,
+                dump=dumped)
+    if not args.full:                                   # the evaluator kernel alone is a run of its own: --full only
+        return d, dt, info
     if req_alone is None:                               # (a lock-step run of fewer than 1024 slots: requests made up from the log's last positions)
         from chinesecheckersagent_amd import _lib as _l
         r_ = np.zeros(n_pos, dtype=_l.REQUEST_DTYPE)
@@ -379,14 +423,35 @@ def config3(args, torch, rank, world, local, barrier):
         req_alone = torch.from_numpy(r_.view(np.uint8).reshape(n_pos, 64)).to('cuda:%d' % local)
         moves_alone = torch.zeros((n_pos, _l.REQUEST_MOVES), dtype=torch.int16, device=req_alone.device)
         asked_now = n_pos
-    k_ms, ev_over_ms = net_kernel_alone(model, req_alone, moves_alone, torch)
-    return d, dt, dict(n_pos=n_pos, k_ms=k_ms, ev_over_ms=ev_over_ms, parts=parts, weights=os.path.basename(w) if w else 'random-init', backend=model.backend,
-                       steps=steps, rows_written=int(rows), file_bytes=size, t_play=t_play, t_drain=t_drain, t_write=t_write,
-                       n_slots=run.n_slots, free_running=bool(getattr(run, 'free_running', False)), asked_in_isolated_batch=asked_now,
-                       net_in_pipeline_ms=(sorted(net_in_pipeline_ms)[len(net_in_pipeline_ms) // 2] if net_in_pipeline_ms else None),
-                       net_in_pipeline_samples=len(net_in_pipeline_ms),
-                       tree_in_pipeline_ms=(sorted(tree_in_pipeline_ms)[len(tree_in_pipeline_ms) // 2] if tree_in_pipeline_ms else None),
-                       host_cpu_s=(ru1.ru_utime + ru1.ru_stime) - (ru0.ru_utime + ru0.ru_stime), peak_rss_mb=ru1.ru_maxrss / 1024.0)
+    info['k_ms'], info['ev_over_ms'] = net_kernel_alone(model, req_alone, moves_alone, torch)
+    info['asked_in_isolated_batch'] = asked_now
+    return d, dt, info
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_rows(directory, sink, rank, world):
+    """--dump-outputs: the rows of the last chunk the sink was handed in the timed region -- the won games of the LAST harvest that
+    finished any (normally the final one: the games that ended in the last `--harvest-every` steps; none finished in the timed
+    region: no rows) -- as board_x, pi_y, v_y and the game id of every row, games in id order (a game's rows in ply order); a fixed,
+    seeded sample of rows if they exceed this rank's share of 64 MB.  -> what the result line says about them (`dump`)"""
+    if sink.last is None:
+        bx, py, vy, games = np.zeros((0, 7, 7, 7)), np.zeros((0, 294)), np.zeros(0), np.zeros(0)
+    else:
+        bx, py, vy, games = (np.asarray(x) for x in sink.last)
+    order = np.argsort(np.asarray(games, dtype=np.int64), kind='stable')
+    rows = len(order)
+    row_bytes = 343 * 4 + 294 * 8 + 8 + 8
+    cap = DUMP_BYTES // world // row_bytes
+    if len(order) > cap:
+        order = order[np.sort(np.random.RandomState(SEED).choice(len(order), cap, replace=False))]
+    os.makedirs(directory, exist_ok=True)
+    prefix = 'rank%d_' % rank if rank else ''
+    for name, a, dt in (('board_x', bx, np.float32), ('pi_y', py, np.float64), ('v_y', vy, np.float64), ('game', games, np.float64)):
+        np.save(os.path.join(directory, prefix + name + '.npy'), np.ascontiguousarray(np.asarray(a)[order], dtype=dt))
+    return {'rows': len(order), 'rows_of_the_harvest': rows, 'games': int(len(np.unique(np.asarray(games)[order]))),
+            'harvest': sink.last_harvest, 'harvests_in_timed_region': sink.harvests}
 
 
 def config2a(args, torch, rank, world, local, barrier, engine, _lib):
@@ -500,9 +565,11 @@ def main():
     # node-expansions/s do not depend on it (+- 0.5 %)
     ap.add_argument('--spread-plies', type=int, default=160, help='untimed plies before the warm-up: the first cohort of games spreads out')
     ap.add_argument('--harvest-every', type=int, default=2)
-    ap.add_argument('--min-seconds', type=float, default=1.0, help='shortest timed region: K more steps are added until it is reached')
     ap.add_argument('--fused-plies', type=int, default=192, help='variant 2a: timed plies of the fused kernel')
-    ap.add_argument('--no-extras', action='store_true', help='headline region only: no variants, config 5, cpu baseline')
+    ap.add_argument('--full', action='store_true', help='beside the headline: the evaluator kernel alone, variants, config 1, config 5, '
+                    'cpu baseline (each a run of its own)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps: the rows of their last harvest as DIR/<name>.npy')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: headline region and the kernel alone only: no variants, config 5, cpu baseline')
     ap.add_argument('--no-config5', action='store_true')
     ap.add_argument('--config5-games', type=int, default=256, help='config 5: self-play games of the iteration (all GPUs together, as NUM_SELF_PLAY is)')
     ap.add_argument('--config5-timeout', type=float, default=300.0, help='N > 1: seconds after which a config 5 that has not come back is given up')
@@ -575,12 +642,12 @@ def main():
         return float(t.item())
 
     G, S, K, W = args.games, args.sims, args.steps, args.warmup
-    extras_wanted = not args.no_extras
+    extras_wanted = args.full and not args.no_extras
 
     # ---- the headline: config 3 through the delivered API (an exception here is fatal: no result line) ----------------
     d3, dt3, info = config3(args, torch, rank, world, local, barrier)
     tot3, _, dt3, per3 = reduce_run(d3, np.zeros(_lib.NUM_ACTIONS, dtype=np.uint64), dt3)
-    k_ms = max_over_ranks(info['k_ms'])
+    k_ms = max_over_ranks(info['k_ms']) if args.full else None
     rows_all, bytes_all = info['rows_written'], info['file_bytes']
     if dist is not None:
         t = torch.tensor([rows_all, bytes_all], dtype=torch.int64, device=coll_dev)
@@ -593,14 +660,13 @@ def main():
         dist.all_gather(every, t)
         host = [[float(x) for x in e.tolist()] for e in every]
     # (the in-pipeline launches are timed between a pair of events each: the pair's own cost, measured on the same launches alone, is taken off)
-    k_in_local = (info['net_in_pipeline_ms'] - info['ev_over_ms']) if info.get('net_in_pipeline_ms') else (info['t_play'] / (info['steps'] * (S + 1) * info['parts']) * 1e3)
+    k_in_local = (info['net_in_pipeline_ms'] - (info['ev_over_ms'] or 0.0)) if info.get('net_in_pipeline_ms') else (info['t_play'] / (info['steps'] * (S + 1) * info['parts']) * 1e3)
     k_in_all = max_over_ranks(k_in_local)
 
     out = None
     if rank == 0:
         ex = tot3['expansions']
         steps = info['steps']
-        tf = info['n_pos'] * NET_FLOP_PER_EVAL / (k_ms * 1e-3) / 1e12
         done = tot3['games_won'] + tot3['games_discarded']
         launches = steps * (S + 1) * info['parts']                      # evaluator launches of one rank in the timed region
         hits = tot3.get('cache_hits', 0)
@@ -627,6 +693,8 @@ def main():
                        'host_cores_per_rank': max(h[0] for h in host) / dt3, 'host_peak_rss_mb_per_rank': max(h[1] for h in host),
                        'free_running': info['free_running'], 'half_batches': info['parts'], 'harvest_every_steps': args.harvest_every,
                        'untimed_steps_before': args.spread_plies + W,
+                       # False in a --dump-outputs run only: no time cap or deadline on ccsp_advance, timed steps included (slower)
+                       'advance_time_limits': not args.dump_outputs,
                        'step': 'sims + 1 = %d evaluator launches per half-batch (a slot plays %.2f searched plies in it)'
                                % (S + 1, tot3['mcts_plies'] / max(steps * info['n_slots'] * world, 1))},
             'description': 'config 3: %d concurrent games/GPU x %d sims/move, %s through the fused fp32-MFMA evaluator kernel (float64 PUCT tree), played '
@@ -664,6 +732,10 @@ def main():
                                      asked_rows_in_isolated_batch=info.get('asked_in_isolated_batch')),
         }
         out['roofline']['event_pair_overhead_ms'] = info['ev_over_ms']        # taken off avg_launch_ms (raw median: + this)
+        if args.dump_outputs:
+            out['dump'] = dict(info['dump'], dir=args.dump_outputs)        # (rank 0's rows; rank r > 0: DIR/rank<r>_<name>.npy)
+        if not args.full and info.get('net_in_pipeline_ms'):
+            out['roofline']['how'] += ' -- without --full: the raw median (the event pair\'s cost is measured on the kernel alone)'
         try:                                 # HBM bytes of one launch by the counters (static: a --pmc pass cannot run inside this process)
             prof = json.load(open(os.path.join(ROOT, 'profiles', 'counters.json')))['net_forward_kernel']
             if info['n_pos'] == prof['n']:

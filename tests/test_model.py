@@ -392,7 +392,7 @@ def test_gpu_all_three_weight_files_on_the_wide_fixture(golden_dir):
     import net_wide_ref
     from chinesecheckersagent_amd.model import ResidualCNN
     z = net_wide_ref.fixture()
-    ref = net_wide_ref.reference_logits(cache='/tmp/n1_wide_ref.npz')
+    ref = net_wide_ref.reference_logits()
     x = torch.from_numpy(z['planes'].reshape(-1, 7, 7, 7).astype(np.float32)).cuda()
     above = total = 0
     for name in net_wide_ref.NAMES:

@@ -81,12 +81,12 @@ def test_weight_file_layout_roundtrip(golden_dir, tmp_path):
     assert set(a) == set(b) and all(np.array_equal(a[k], b[k]) for k in a)           # float32 values unchanged
     ResidualCNN(device='cpu').load_weights(path)                                      # and the product loads it
     conda = '/opt/conda/bin/python3.9'
-    if os.path.exists(conda) and os.path.exists('/root/reference/good_model.h5'):     # real HDF5 library, reference layout
-        code = ("import h5py,sys; a=h5py.File('/root/reference/good_model.h5','r'); b=h5py.File(sys.argv[1],'r'); "
+    if os.path.exists(conda):           # real HDF5 library, reference layout (tests/golden/good_model.h5 is the reference's file)
+        code = ("import h5py,sys; a=h5py.File(sys.argv[2],'r'); b=h5py.File(sys.argv[1],'r'); "
                 "assert list(a.attrs['layer_names'])==list(b.attrs['layer_names']); "
                 "assert all(list(a[n.decode()].attrs['weight_names'])==list(b[n.decode()].attrs['weight_names']) for n in a.attrs['layer_names']); "
                 "print('same layout')")
-        assert 'same layout' in subprocess.check_output([conda, '-c', code, path]).decode()
+        assert 'same layout' in subprocess.check_output([conda, '-c', code, path, golden_dir + '/good_model.h5']).decode()
 
 
 def test_train_function_and_fit(golden_dir, tmp_path):

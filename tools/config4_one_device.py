@@ -3,7 +3,7 @@ This process never touches the GPU; it starts
   (1) selfplay.generate_self_play_in_parallel with `ranks` rank processes on device 0 (gloo summary), each 4096 free-running slots x 400
       simulations with good_model.h5, for `steps` steps (a bounded rehearsal: the full shape plays for minutes on a shared device), rows
       streamed into the ranks' files;
-  (2) `CCSP_BENCH_ONE_DEVICE=1 python bench.py --gpus <ranks> --games 512` with the driver's other defaults: wall time against its timeout.
+  (2) `CCSP_BENCH_ONE_DEVICE=1 python bench.py --gpus <ranks> --games 512 --full` with the driver's other defaults: wall time against its timeout.
 The pool admits SIX processes on a card at once (process guard): `ranks` <= 6, BASELINE's eight cannot be started on a 1-GPU box.
     python tools/config4_one_device.py [ranks=6] [steps=40] [bench: 1|0]"""
 import json, os, resource, subprocess, sys, tempfile, time
@@ -43,7 +43,7 @@ print('host budget: %d usable cores / %d ranks = %.2f per rank (a rank needs ~1.
 if with_bench:
     env = dict({k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}, CCSP_BENCH_ONE_DEVICE='1')
     t0 = time.time()
-    r = subprocess.run([sys.executable, 'bench.py', '--gpus', str(ranks), '--games', '512'], env=env, capture_output=True, text=True, timeout=1500)
+    r = subprocess.run([sys.executable, 'bench.py', '--gpus', str(ranks), '--games', '512', '--full'], env=env, capture_output=True, text=True, timeout=1500)
     dt = time.time() - t0
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     print('bench.py --gpus %d --games 512 (all ranks on device 0, gloo; every other flag the driver\'s default): exit %d, %d JSON line(s), wall %.1f s'

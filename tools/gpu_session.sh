@@ -6,12 +6,14 @@ tag=$1; shift
 cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 mkdir -p gpurun_out
+logs=$_                 # the log directory: the argument of the mkdir right above (keep the two lines together)
+[ -d "$logs" ] || { echo "gpu_session.sh: no log directory" >&2; exit 1; }
 run() { # name seconds command...
   local name=$1 secs=$2; shift 2
   echo "=== $name ($(date +%T))"
-  timeout -k 10 "$secs" "$@" > gpurun_out/${tag}_$name.log 2>&1
+  timeout -k 10 "$secs" "$@" > "$logs/${tag}_$name.log" 2>&1
   local rc=$?
-  echo "=== $name rc=$rc"; tail -n 12 gpurun_out/${tag}_$name.log
+  echo "=== $name rc=$rc"; tail -n 12 "$logs/${tag}_$name.log"
   if [ $rc -ge 124 ]; then echo "step $name was killed: session ends"; exit $rc; fi
   return 0
 }
@@ -19,12 +21,12 @@ for step in "$@"; do
   case $step in
     tests) run tests 900 python3 -m pytest tests -m gpu -x -q ;;
     tests_all) run tests 900 python3 -m pytest tests -m gpu -q ;;
-    bench) run bench 600 python3 bench.py; grep '^{' gpurun_out/${tag}_bench.log > gpurun_out/${tag}_bench.json ;;
-    stats) rm -rf /tmp/st_$tag; run stats 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/st_$tag -- python3 bench.py --steps 20 --warmup 5 --spread-plies 16 --no-extras
-           grep '^{' gpurun_out/${tag}_stats.log > gpurun_out/${tag}_bench_under_rocprof.json
-           f=$(find /tmp/st_$tag -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" gpurun_out/${tag}_bench_kernel_stats.csv
-           f=$(find /tmp/st_$tag -name "*kernel_trace.csv" | head -1)      # every launch of the multi-ply kernel with its own duration
-           [ -n "$f" ] && python3 - "$f" > gpurun_out/${tag}_launches.csv <<'PY'
+    bench) run bench 600 python3 bench.py --full; grep '^{' "$logs/${tag}_bench.log" > "$logs/${tag}_bench.json" ;;
+    stats) rm -rf "$TMPDIR/st_$tag"; run stats 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$TMPDIR/st_$tag" -- python3 bench.py --steps 20 --warmup 5 --spread-plies 16 --full --no-extras
+           grep '^{' "$logs/${tag}_stats.log" > "$logs/${tag}_bench_under_rocprof.json"
+           f=$(find "$TMPDIR/st_$tag" -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" "$logs/${tag}_bench_kernel_stats.csv"
+           f=$(find "$TMPDIR/st_$tag" -name "*kernel_trace.csv" | head -1)      # every launch of the multi-ply kernel with its own duration
+           [ -n "$f" ] && python3 - "$f" > "$logs/${tag}_launches.csv" <<'PY'
 import csv, sys
 print('kernel,start_ns,duration_ms')
 rows = []
