@@ -459,6 +459,56 @@ __device__ __forceinline__ void gemm_tiles_split(const WBuf &wb, int wbase, int 
     }
 }
 
+// <8, 8> (round 7, CCSP_NET_TAIL_4X4): the last row tile of the 3x3 layers is the 25th cell -- 8 real rows and 8 of padding -- and half of
+// every 16x16x4 instruction spent on it multiplies padding.  v_mfma_f32_4x4x1_16B_f32 has no empty rows at 8 positions (the policy dense
+// layer runs on it for that reason): its sixteen 4 x 4 blocks are taken as 2 row groups x 8 column groups = 8 rows x 32 columns for ONE k, so
+// one wave covers BOTH column tiles of a k-segment at the cost of one 16x16 column tile (16 instructions of 8 cycles per k-block against
+// 4 of 32): four segment jobs per layer instead of eight.
+//   lane l supplies the activation of row 4 ((l >> 2) & 1) + (l & 3) (= the position) and the weight of column 4 (l >> 3) + (l & 3);
+//   reg r of its result is row 4 ((l >> 2) & 1) + r of that column.
+// THE BITS ARE THE SAME: both instructions are chains of fused multiply-adds with one rounding per k (tools/probe/mfma_tail_probe.hip: both
+// equal to a plain fmaf chain on the host, bit for bit, K = 64 and 80, denormals and signed zeros included), and the chain runs in the
+// order the 16x16x4 form has -- k-block kb, step j, k-slot q: k = 16 kb + 4 q + j -- from a zero accumulator.
+// Operands: ya = the lane's row of y1 at its top-left tap, channel 0 (one ds_read_b128 per k-slot q: channels 16 (kb & 1) + 4 q + 0..3, the
+// two row groups' lanes of a column share nothing, the eight column groups of a row read the same address: broadcast); the weights from the
+// layer's ordinary packed order [nt][kb][lane][j] through wbt, whose per-lane offset names (column tile, column) and whose scalar offset
+// names (kb, q) -- 16 bytes = W[16 kb + 4 q + 0..3][column].  Nothing but DS reads, buffer loads and MFMAs in the loop.
+#ifndef CCSP_NET_TAIL_4X4
+#define CCSP_NET_TAIL_4X4 1
+#endif
+template <int KB0, int KBN, typename AFrag>
+__device__ __forceinline__ f32x4 tail_tile_4x4(const WBuf &wbt, int wbase /* the layer's packed weights: float offset, scalar */, AFrag afrag /* (kb, q) */) {
+    constexpr int NBQ = 3;                                               // weight ring: NBQ - 1 k-blocks in flight
+    static_assert(KBN >= NBQ, "a segment is four or five k-blocks");
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 a[2][4], b[NBQ][4];
+#pragma unroll
+    for (int d = 0; d < NBQ - 1; d++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) b[d][q] = wbt.load(wbase + (KB0 + d) * 256 + q * 64);
+#pragma unroll
+    for (int q = 0; q < 4; q++) a[0][q] = afrag(KB0, q);
+#pragma unroll
+    for (int i = 0; i < KBN; i++) {
+        if (i + NBQ - 1 < KBN) {
+#pragma unroll
+            for (int q = 0; q < 4; q++) b[(i + NBQ - 1) % NBQ][q] = wbt.load(wbase + (KB0 + i + NBQ - 1) * 256 + q * 64);
+        }
+        if (i + 1 < KBN) {
+#pragma unroll
+            for (int q = 0; q < 4; q++) a[(i + 1) & 1][q] = afrag(KB0 + i + 1, q);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+#pragma unroll
+            for (int q = 0; q < 4; q++) acc = __builtin_amdgcn_mfma_f32_4x4x1f32(a[i & 1][q][j], b[i % NBQ][q][j], acc, 0, 0, 0);
+#if CCSP_NET_KB_FENCE
+        __builtin_amdgcn_sched_barrier(0);
+#endif
+    }
+    return acc;
+}
+
 // <1, 8> (Cfg::ALLSPLIT): a wave's whole share of a 3x3 layer is a 1/NSH part of ONE tile's k-range -- whole segments of the same NSEG
 // chains as everywhere else (kpart * SPW .. + SPW - 1; the segments of every part are equally long: asserted), their raw sums to `part`
 // for the next layer to add up in the fixed order.  The part's k-blocks start at a wave-uniform RUNTIME index: afrag(kb) and the weight
@@ -777,6 +827,26 @@ __global__ __launch_bounds__(C::NTH) void net_forward_kernel(const float *__rest
     const lds_float *const y2r = lds_opaque(&S.y2[(((wave >> 2) * M64) * 16 + l15) * LDY + 4 * q]);      // ... as the last 1x1 layer reads it
     lds_float *const partw = lds_opaque(&S.part[AS ? mt3 * 2 + nt2 : nt2][(AS ? kh : (XT ? kshare : 0)) * (C::NSEG / C::NSH)][lane * 4]);
     const lds_float *const partr = lds_opaque(&S.part[AS ? ((wave >> 2) * M64) * 2 : 0][0][lane * 4]);
+    // <8, 8>: the last tile of the 3x3 layers on 4 x 4 MFMAs (tail_tile_4x4) -- four segment jobs, segment w on wave w = 0 .. 3: one per SIMD
+    // (waves w and w + 4 share one), and the wave of the two that the SIMD serves FIRST: in the stamps (profiles/r7_net_tail_tile.txt) waves
+    // 0-3 are through a 3x3 layer after 8 k of its 13 k ticks and waves 4-7 end it.  The job is ONE dependent chain (14 cycles per
+    // instruction where 8 would do) behind a round trip for its operands, 2.5-3.5 k ticks for the wave that runs it: measured on waves 5
+    // and 7 it lengthened the layer's critical path and gained nothing there, and in FRONT of the wave's own tiles (waves 0-3) it gained a
+    // sixth of what it gains behind them.
+    constexpr bool TAIL4 = NB == 8 && CM && XT == 1 && CCSP_NET_TAIL_4X4 != 0;
+    static_assert(!TAIL4 || (C::NSEG == 4 && NSPLIT == 4), "one segment job on each of the waves 0 .. 3");
+    const int trow = 4 * ((lane >> 2) & 1) + (lane & 3), tcol = 4 * (lane >> 3) + (lane & 3);    // the lane's row (position) and column
+    WBuf wbt = wb;
+    wbt.voff = ((tcol >> 4) * 18 * 256 + (tcol & 15) * 4) * 4;                                   // [nt][kb][lane' = 16 q + (col & 15)][j]: nt and col & 15
+    const lds_float *ytail = nullptr;
+    lds_float *partt = nullptr;
+    if constexpr (TAIL4) {
+        constexpr int pos = CELL8[24];
+        ytail = lds_opaque(&S.y1[((6 * (pos / 5) + pos % 5 + CM_PAD - 7) * NB + trow) * LDY]);   // y1_at(trow, pos, true) without the k-slot
+        // the raw segment sums in the order the last 1x1 layer reads as an activation fragment (ax[kb], partr): k-block = column tile, lane'
+        // = 16 (k-slot) + row, j: part[col >> 4][segment][(16 ((col >> 2) & 3) + row) * 4 + (col & 3)]; the lane's four rows are 16 bytes apart
+        partt = lds_opaque(&S.part[tcol >> 4][0][(16 * ((tcol >> 2) & 3) + 4 * ((lane >> 2) & 1)) * 4 + (tcol & 3)]);
+    }
 
     // ---- nine bottleneck residual blocks (model.py:120-145) ------------------------------------------
     f32x4 bq2[AS ? 18 / C::NSH : 1];                             // (AS: this wave's weight k-blocks of the block's 3x3 layer)
@@ -840,6 +910,26 @@ __global__ __launch_bounds__(C::NTH) void net_forward_kernel(const float *__rest
                 if constexpr (CM) {                               // one straight-line copy of the layer per row group (= map edge)
                     auto run = [&](auto G) {
                         constexpr int g = decltype(G)::value;
+                        if constexpr (TAIL4) {
+                            // the wave's own tiles with no share of the last one (KPARTC = -1); then, on waves 0 .. 3, the last tile's segment
+                            // job, both column tiles at once (by then the layer's weights have been through L2 once, and the partner wave of
+                            // the SIMD -- which ends the layer -- has the pipe while the job's operands arrive)
+                            gemm_tiles_split<F32A, 18, C::NSEG, NSPLIT, C::NE, true, C::dead_of(g, 0), C::dead_of(g, 1), -1>(wb, (LAY.l2_w[0] + wo), nt2, mt3, MT - 1, 0, pre, afrag, next, epi, partw);
+                            if constexpr (g < 2) {
+                                auto afrag4 = [&](int kb, int q4) -> f32x4 {
+                                    const int tap = kb >> 1;
+                                    return lds_load4(ytail, ((tap / 3) * 6 + tap % 3) * TAPROW + (kb & 1) * 16 + 4 * q4);
+                                };
+                                auto job = [&](auto SEG) {
+                                    constexpr int seg = decltype(SEG)::value, kb0 = (18 * seg) / C::NSEG, kb1 = (18 * (seg + 1)) / C::NSEG;
+                                    const f32x4 t = tail_tile_4x4<kb0, kb1 - kb0>(wbt, (LAY.l2_w[0] + wo), afrag4);
+#pragma unroll
+                                    for (int r = 0; r < 4; r++) partt[seg * 256 + r * 4] = t[r];
+                                };
+                                if (nt2 == 0) job(std::integral_constant<int, 2 * g>{});      // wave = 2 g + nt2 = its segment
+                                else job(std::integral_constant<int, 2 * g + 1>{});
+                            }
+                        } else
                         gemm_tiles_split<F32A, 18, C::NSEG, NSPLIT, C::NE, true, C::dead_of(g, 0), C::dead_of(g, 1), C::xseg_of(g)>(wb, (LAY.l2_w[0] + wo), nt2, mt3, MT - 1, 0, pre, afrag, next, epi, partw);
                     };
                     if (qr == 0) run(std::integral_constant<int, 0>{});
