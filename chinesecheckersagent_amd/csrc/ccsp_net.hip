@@ -367,6 +367,62 @@ __device__ __forceinline__ void gemm_tiles(const WBuf &wb, int wbase, int nt, in
     }
 }
 
+// <8, 8> (round 8, CCSP_NET_TILE_GROUPS; 0 = gemm_tiles as before): a 64-column layer (the blocks' last 1x1) with a wave's NMT tiles in
+// TWO GROUPS, G1 + (NMT - G1): group 1 through all k-blocks, then group 2 -- whose first A fragments are read during group 1's last
+// k-block -- and the epilogues (bias, residual, ReLU, one ds_write_b128 per tile) behind next() as before: the scheduler places group
+// 1's between group 2's MFMAs, and the wave of a SIMD that ends the layer alone (waves 4-7: see the stamps) has three epilogues behind
+// its last MFMA instead of six.  (By the stamps that tail is hardly shorter; the older wave no longer runs its epilogues into the
+// partner's MFMA stream, and the younger wave's stream ends 0.2 k ticks earlier.)  The layer's KB weight k-blocks stay in registers across both groups; the A double buffer is G1
+// wide instead of NMT.  Every output is the chain it was (k-block, step j, k-slot q from a zero accumulator, bias behind the sum): only
+// the order BETWEEN tiles changes.  A fence between the groups (the max-ILP scheduler merges them otherwise).
+// Measured (profiles/r8_net_wave_pairing.txt): the nine last 1x1 layers 50.5 k -> 46.0 k ticks of a workgroup's 240 k, the headline + 1.0
+// .. + 1.8 %.  CCSP_NET_TILE_GROUPS = 2 (5 + 2 and 4 + 2 tiles): 44.9 - 45.5 k ticks, the headline the same.  The stem (K = 80) in groups
+// (CCSP_NET_TILE_GROUPS_STEM = 1) is no shorter -- 11.1 k -> 11.2 k ticks, 11.4 k with 5 + 2 -- and stays on gemm_tiles.
+#ifndef CCSP_NET_TILE_GROUPS
+#define CCSP_NET_TILE_GROUPS 1
+#endif
+#ifndef CCSP_NET_TILE_GROUPS_STEM
+#define CCSP_NET_TILE_GROUPS_STEM 0
+#endif
+template <int NMT, int G1, int KB, typename AFrag, typename Next, typename Epi>
+__device__ __forceinline__ void gemm_tiles_grouped(const WBuf &wb, int wbase, int nt, int mt0, f32x4 (&pre)[NPREMAX], AFrag afrag, Next next, Epi epi) {
+    constexpr int NPRE = Pre<KB>::N, G2 = NMT - G1;
+    static_assert(G2 >= 1 && G1 >= G2, "two groups, the first at least as large as the second");
+    const int w0 = wbase + nt * KB * 256;
+    f32x4 bq[KB];
+#pragma unroll
+    for (int d = 0; d < KB; d++) {
+        if (d < NPRE) bq[d] = pre[d];
+        else bq[d] = wb.load(w0 + d * 256);
+    }
+    f32x4 acc[NMT];
+#pragma unroll
+    for (int i = 0; i < NMT; i++) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 a[2][G1];
+#pragma unroll
+    for (int i = 0; i < G1; i++) a[0][i] = afrag(mt0 + i, 0, i);
+#pragma unroll
+    for (int s = 0; s < 2 * KB; s++) {                                  // step s: k-block s % KB of group s / KB, A fragments in buffer s & 1
+        const int kb = s % KB, i0 = s < KB ? 0 : G1, n = s < KB ? G1 : G2;
+        if (s + 1 < 2 * KB) {
+            const int j0 = s + 1 < KB ? 0 : G1, m = s + 1 < KB ? G1 : G2;
+#pragma unroll
+            for (int i = 0; i < m; i++) a[(s + 1) & 1][i] = afrag(mt0 + j0 + i, (s + 1) % KB, j0 + i);   // one step ahead (LDS latency)
+        }
+        const f32x4 b = bq[kb];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+#pragma unroll
+            for (int i = 0; i < n; i++)
+                acc[i0 + i] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[j], a[s & 1][i][j], acc[i0 + i], 0, 0, 0);   // D^T: see tile_out
+        }
+        if (s == KB - 1) __builtin_amdgcn_sched_barrier(0);
+    }
+    next();
+#pragma unroll
+    for (int i = 0; i < NMT; i++) epi(mt0 + i, acc[i], i);
+}
+
 // The 32-column layers have 13 x 2 = 26 tile jobs for 8 waves.  Instead of four jobs on every wave (two of the
 // 32 slots duplicated, four phantom), a wave takes THREE full row tiles of its column tile and a quarter of the
 // k-range of row tile 12 (xmt) of the same column tile -- same weight stream, 3.25 jobs' worth of MFMAs instead of
@@ -635,9 +691,12 @@ __device__ unsigned long long net_stamps[64];
 __device__ unsigned long long net_stamps2[8][8];          // [wave][point] inside block 4's last 1x1 layer
 #define NET_STAMP(i) do { if (blockIdx.x == 0 && threadIdx.x == 0) net_stamps[i] = __builtin_amdgcn_s_memtime(); } while (0)
 #define NET_STAMP2(pt) do { if (blockIdx.x == 0 && lane == 0 && blk == 4) net_stamps2[wave][pt] = __builtin_amdgcn_s_memtime(); } while (0)
+__device__ unsigned long long net_stamps3[8][8];          // [wave][point] inside block 4's first 1x1 layer (the same five points)
+#define NET_STAMP3(pt) do { if (blockIdx.x == 0 && lane == 0 && blk == 4) net_stamps3[wave][pt] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
 #define NET_STAMP(i) do { } while (0)
 #define NET_STAMP2(pt) do { } while (0)
+#define NET_STAMP3(pt) do { } while (0)
 #endif
 
 // REQ (the free-running path's hand-off, ccsp_net_forward_requests): the input is the batch of REQUEST records -- the position, 64 bytes
@@ -767,6 +826,15 @@ __global__ __launch_bounds__(C::NTH) void net_forward_kernel(const float *__rest
         else return *reinterpret_cast<const f32x4 *>(W + LAY.trunk_b + idx + 4 * q);
     };
     auto relu4 = [](const f32x4 &v) -> f32x4 { return f32x4{relu(v[0]), relu(v[1]), relu(v[2]), relu(v[3])}; };
+    // <8, 8>, round 8 (profiles/r8_net_wave_pairing.txt).  GROUPS: the blocks' last 1x1 in two tile groups (gemm_tiles_grouped), 4 + 3
+    // tiles in the first row half and 3 + 3 in the second (CCSP_NET_TILE_GROUPS = 2: 5 + 2 and 4 + 2); the tile that arrives as partial
+    // sums (XSLOT below) is in the last group.  (Tried with it and dropped: s_setprio 1 on entering a layer of the block loop, 0 from a
+    // quarter / half / three quarters of its k-blocks on.  The two waves of a SIMD then end a 3x3 layer together -- and the layer is 0.1
+    // - 0.7 k ticks LONGER, the 1x1 layers 0.1 k shorter each; the headline within the parent's spread (a quarter, a half) or 3 % lower
+    // (three quarters), the tree kernels' idle rows up.)
+    constexpr bool GROUPS = NB == 8 && NW == 8 && CCSP_NET_TILE_GROUPS != 0 && CCSP_NET_SEG_L3 == 1;
+    constexpr bool GROUPS_STEM = GROUPS && CCSP_NET_TILE_GROUPS_STEM != 0 && CCSP_NET_SEG_STEM == 1;
+    constexpr auto group1 = [](int tiles) { return CCSP_NET_TILE_GROUPS == 2 ? tiles - 2 : (tiles + 1) / 2; };
 
     // The trunk's tiles have the same owner in the stem and in every block's last layer (column tile wave & 3, row tiles 6 (wave >> 2)
     // .. + 6): the owner keeps its seven tiles in registers as well, so that the residual add needs no LDS read.
@@ -801,6 +869,10 @@ __global__ __launch_bounds__(C::NTH) void net_forward_kernel(const float *__rest
         };
         prefetch<5>(wb, LAY.stem_w, nt, pre);
         auto next = [&]() { prefetch<4>(wb, LAY.l1_w[0], nt2, pre); };
+        if constexpr (GROUPS_STEM) {
+            if ((wave >> 2) == 0) gemm_tiles_grouped<F64, group1(F64), 5>(wb, LAY.stem_w, nt, mt0, pre, afrag, next, epi);
+            else gemm_tiles_grouped<F64B, group1(F64B), 5>(wb, LAY.stem_w, nt, mt0, pre, afrag, next, epi);
+        } else
         if (F64B == F64 || (wave >> 2) == 0) gemm_tiles<F64, 5, CCSP_NET_SEG_STEM>(wb, LAY.stem_w, nt, mt0, pre, afrag, next, epi);
         else gemm_tiles<F64B, 5, CCSP_NET_SEG_STEM>(wb, LAY.stem_w, nt, mt0, pre, afrag, next, epi);
     }
@@ -855,6 +927,7 @@ __global__ __launch_bounds__(C::NTH) void net_forward_kernel(const float *__rest
         int n2o = nt2 * 16;                                                      // (opaque per block: the sum y1p[i] + n2o is formed where it is used --
         asm volatile("" : "+s"(n2o));                                            //  one v_add per tile and layer -- not kept in a register per tile)
         {   // 1x1 64 -> 32: 2 column tiles x 4 row groups of three tiles + a quarter of tile 12's k-range each
+            NET_STAMP3(0);
             auto afrag = [&](int, int kb, int i) -> f32x4 {                     // (slot i: row tile mt3 + i; slot F32A: the last tile)
                 return i < F32A ? lds_load4(xin, i * 16 * LDX + kb * 16) : lds_load4(xinx, kb * 16);
             };
@@ -879,16 +952,19 @@ __global__ __launch_bounds__(C::NTH) void net_forward_kernel(const float *__rest
                 if (kh == 0) gemm_tiles<1, 4, CCSP_NET_SEG_L1>(wb, (LAY.l1_w[0] + wo), nt2, mt3, pre, afrag, []() {}, epi1);
             } else
             {
-                auto next = [&]() { prefetch<18>(wb, (LAY.l2_w[0] + wo), nt2, pre); };
+                auto next = [&]() { NET_STAMP3(2); prefetch<18>(wb, (LAY.l2_w[0] + wo), nt2, pre); };
+                NET_STAMP3(1);
                 if constexpr (CM && NB < 8) {                    // a copy of the layer with the last tile, one without (gemm_tiles_last).  A/B on one
                                                                  // box, round 5: <4,4> 68.3 -> 67.7 us per 1024 positions; <8,8> (two waves per SIMD) 103.8 -> 105.3: not there
                     if (kshare == NSPLIT - 1) gemm_tiles_last<F32A, 4, NSPLIT, CCSP_NET_SEG_L1, 1>(wb, (LAY.l1_w[0] + wo), nt2, mt3, MT - 1, kshare, pre, afrag, next, epi, epix);
                     else gemm_tiles_last<F32A, 4, NSPLIT, CCSP_NET_SEG_L1, 0>(wb, (LAY.l1_w[0] + wo), nt2, mt3, MT - 1, kshare, pre, afrag, next, epi, epix);
                 } else
                     gemm_tiles_last<F32A, 4, NSPLIT, CCSP_NET_SEG_L1, -1>(wb, (LAY.l1_w[0] + wo), nt2, mt3, MT - 1, kshare, pre, afrag, next, epi, epix);
+                NET_STAMP3(3);
             }
         }
         __syncthreads();
+        NET_STAMP3(4);
         NET_STAMP(2 + 3 * blk);
         {   // 3x3 same 32 -> 32: k-block kb = tap (kb >> 1), channels 16 (kb & 1) ..; the halo supplies the zeros
             auto afrag = [&](int, int kb, int i) -> f32x4 {
@@ -983,6 +1059,11 @@ __global__ __launch_bounds__(C::NTH) void net_forward_kernel(const float *__rest
                 // (no branch: the same three loads either way -- the next block's first 1x1 or, behind the last block, the policy conv)
                 prefetch<4>(wb, blk < 8 ? LAY.l1_w[0] + wo + BLK_STRIDE : LAY.pc_w, blk < 8 ? nt2 : 0, pre);
             };
+            if constexpr (GROUPS) {
+                static_assert(!GROUPS || XSLOT >= group1(F64B), "the tile fed from Smem::part is in the last group");
+                if (half == 0) gemm_tiles_grouped<F64, group1(F64), 2>(wb, (LAY.l3_w[0] + wo), nt, mt0, pre, afrag, next, epi);
+                else gemm_tiles_grouped<F64B, group1(F64B), 2>(wb, (LAY.l3_w[0] + wo), nt, mt0, pre, afrag, next, epi);
+            } else
             if (F64B == F64 || half == 0) gemm_tiles<F64, 2, CCSP_NET_SEG_L3>(wb, (LAY.l3_w[0] + wo), nt, mt0, pre, afrag, next, epi);
             else gemm_tiles<F64B, 2, CCSP_NET_SEG_L3>(wb, (LAY.l3_w[0] + wo), nt, mt0, pre, afrag, next, epi);
             NET_STAMP2(3);
@@ -1306,8 +1387,10 @@ int ccsp_net_forward_requests(const float *packed, const ccsp_request *req, cons
 #ifdef CCSP_STAMPS
 int ccsp_debug_net_stamps(unsigned long long *out) {
     const bool more = out[63] == 0x5eedULL;            // (the caller passes 128 words and says so)
+    const bool more3 = more && out[62] == 0x5eedULL;   // (... or 192)
     CCSP_HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(net_stamps), 64 * sizeof(unsigned long long)));
     if (more) CCSP_HIPCHK(hipMemcpyFromSymbol(out + 64, HIP_SYMBOL(net_stamps2), 64 * sizeof(unsigned long long)));
+    if (more3) CCSP_HIPCHK(hipMemcpyFromSymbol(out + 128, HIP_SYMBOL(net_stamps3), 64 * sizeof(unsigned long long)));
     return CCSP_OK;
 }
 #endif

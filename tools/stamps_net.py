@@ -1,11 +1,13 @@
 """Diagnostic: where workgroup 0 of net_forward_kernel spends its time (s_memtime at the layer boundaries; a
-SEPARATE build, never timed for throughput).  Usage on the GPU box: python tools/stamps_net.py"""
+SEPARATE build, never timed for throughput).  Usage on the GPU box: python tools/stamps_net.py [-DFLAG ...]
+STAMPS_LIB=<library built with -DCCSP_STAMPS, e.g. by tools/build_variant.sh <name> ccsp_net.hip -DCCSP_STAMPS ...>: use it, compile nothing."""
 import os, subprocess, sys, ctypes as C
 sys.path.insert(0, '.')
 here = 'chinesecheckersagent_amd'
-so = os.path.join(here, 'libccsp_stamps.so')
-subprocess.check_call(['hipcc', '--offload-arch=gfx950', '-O3', '-ffp-contract=off', '-fPIC', '-std=c++17', '-shared', '-DCCSP_STAMPS'] + sys.argv[1:] +
-                      ['-o', so] + [os.path.join(here, 'csrc', f) for f in ('ccsp_rules_kernels.hip', 'ccsp_engine.hip', 'ccsp_net.hip', 'ccsp_host.hip')])
+so = os.environ.get('STAMPS_LIB') or os.path.join(here, 'libccsp_stamps.so')
+if not os.environ.get('STAMPS_LIB'):
+    subprocess.check_call(['hipcc', '--offload-arch=gfx950', '-O3', '-ffp-contract=off', '-fPIC', '-std=c++17', '-shared', '-DCCSP_STAMPS'] + sys.argv[1:] +
+                          ['-o', so] + [os.path.join(here, 'csrc', f) for f in ('ccsp_rules_kernels.hip', 'ccsp_engine.hip', 'ccsp_net.hip', 'ccsp_host.hip')])
 import torch, numpy as np
 from chinesecheckersagent_amd import _lib
 _lib.LIB_PATH = so
@@ -18,8 +20,8 @@ m = ResidualCNN(backend='hip'); m.load_weights('tests/golden/good_model.h5')
 for _ in range(3):
     m.evaluate_batch(x)
 torch.cuda.synchronize()
-out = (C.c_ulonglong * 128)()
-out[63] = 0x5eed
+out = (C.c_ulonglong * 192)()
+out[62] = out[63] = 0x5eed                                     # (192 words: net_stamps, net_stamps2, net_stamps3)
 L = _lib.lib()
 L.ccsp_debug_net_stamps.restype = C.c_int
 assert L.ccsp_debug_net_stamps(out) == 0
@@ -54,3 +56,11 @@ t00 = min(r[0] for r in s2)
 print('last 1x1 of block 4, per wave (ticks after the first wave entered the layer): start / sums / MFMAs issued / epilogue / past barrier')
 for w in range(8):
     print('  wave %d: %s' % (w, ' '.join('%6d' % (x - t00) for x in s2[w])))
+
+# round 8: the same five points inside block 4's FIRST 1x1 layer: [0] layer start, [1] bias and lambdas set up: in front of the GEMM,
+# [2] last MFMA issued, [3] epilogue done, [4] past the barrier
+s3 = [[int(out[128 + w * 8 + k]) for k in range(5)] for w in range(8)]
+t00 = min(r[0] for r in s3)
+print('first 1x1 of block 4, per wave (ticks after the first wave entered the layer): start / at the GEMM / MFMAs issued / epilogue / past barrier')
+for w in range(8):
+    print('  wave %d: %s' % (w, ' '.join('%6d' % (x - t00) for x in s3[w])))
